@@ -73,6 +73,16 @@ def cache_dir():
 N_CHROMS = 8
 
 
+def put_last_wins(G, idx, vals):
+    """G[idx] = vals where idx repeats (overlapping copies): the write of the last occurrence of a position wins.  A plain index_put on the
+    GPU keeps an arbitrary one of the repeated writes, which made the genome -- and the reads drawn from it -- differ from run to run."""
+    import torch
+    idx, order = torch.sort(idx, stable=True)
+    last = torch.ones_like(idx, dtype=torch.bool)
+    last[:-1] = idx[1:] != idx[:-1]
+    G[idx[last]] = vals[order[last]]
+
+
 def synth_genome_gpu(mbp, seed, device):
     """Deterministic hg38-like synthetic genome as one uint8 tensor of codes 0..3 (4 = N) + chromosome lengths.
 
@@ -115,7 +125,7 @@ def synth_genome_gpu(mbp, seed, device):
             rb = torch.randint(1, 4, (kk, L), generator=g, device=device, dtype=torch.uint8)
             vals = torch.where(mut, (vals + rb) % 4, vals)
             dst = start.unsqueeze(1) + off
-            G[dst[keep]] = vals[keep]
+            put_last_wins(G, dst[keep], vals[keep])
 
     def cons(L):
         return torch.randint(0, 4, (L,), generator=g, device=device, dtype=torch.uint8)
@@ -134,7 +144,7 @@ def synth_genome_gpu(mbp, seed, device):
     off = torch.arange(300, device=device).unsqueeze(0)
     keep = off < ln.unsqueeze(1)
     vals = torch.gather(ub, 1, off.expand(k, 300) % unit.unsqueeze(1))
-    G[(start.unsqueeze(1) + off)[keep]] = vals[keep]
+    put_last_wins(G, (start.unsqueeze(1) + off)[keep], vals[keep])
     # segmental duplications (copied from the current state of the sequence)
     k = max(1, int(n * 0.04 / 22_500))
     for _ in range(k):
@@ -1000,6 +1010,72 @@ def synth_pairs_gpu(G, npairs, length, seed, device):
     return seq.contiguous(), qual.contiguous()
 
 
+# ------------------------------------------------------------------------------------------ --dump-outputs ----
+DUMP_READS = 65536            # a batch of more reads is dumped as a fixed, seeded sample of this many
+DUMP_BYTES = 64 << 20         # ... and the sample is cut short where the files would hold more than this
+DUMP_READ_FIELDS = ("status", "aligned", "maxed", "filt", "exhausted", "has_secbest", "pair_type", "pair_flags",
+                    "secbest", "best", "nalns", "nreport", "pair_best", "pair_secbest")
+DUMP_ALN_FIELDS = ("refoff", "reflen", "refid", "score", "ns", "gaps", "edits", "bases_aligned", "refns", "nned",
+                   "rdlen", "rdextent", "rfextent", "trim5p", "trim3p", "fw")
+DUMP_EDIT_FIELDS = ("pos", "chr", "qchr", "type")
+
+
+def dump_sample(n):
+    """The reads whose result records --dump-outputs writes: the whole batch up to DUMP_READS reads, else a fixed seeded sample (in read order)."""
+    import numpy as np
+    if n <= DUMP_READS:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(20240601).choice(n, DUMP_READS, replace=False)).astype(np.int64)
+
+
+def dump_outputs(d, rows, reads, khits):
+    """--dump-outputs: the result records of bt2g_align_batch (bt2g.h: bt2g_read_result, then `nreport` alignment slots of (pad2 >> 16) * 8 bytes),
+    decoded for the sampled reads `reads` (rows: their records, uint8 [m, stride]) into float64 DIR/<name>.npy:
+      read_index [m]                 the read's position in the batch
+      <DUMP_READ_FIELDS> [m]         the record's header
+      aln_<DUMP_ALN_FIELDS> [m, khits]   alignment slot j of the read (0 where j >= nreport)
+      edit_read, edit_slot, edit_<DUMP_EDIT_FIELDS> [E]   one entry per edit of every reported alignment (row of read_index, slot)
+    The work counters and padding of the record are not written: they are not what the alignment computed.
+    Returns (files, bytes, reads written)."""
+    import ctypes as C
+    import numpy as np
+    import bowtie2_amd as b
+    rd, ad, ed = np.dtype(b.ReadResult), np.dtype(b.Aln), np.dtype(b.Edit)
+    hoff, ned_off = rd.fields["alns"][1], ad.fields["ned"][1]
+    sub = lambda dt, names, size: np.dtype({"names": list(names), "formats": [dt.fields[k][0] for k in names],
+                                            "offsets": [dt.fields[k][1] for k in names], "itemsize": size})
+    hdr = np.ascontiguousarray(rows[:, :hoff]).view(sub(rd, DUMP_READ_FIELDS + ("pad2",), hoff))[:, 0]
+    head_dt = sub(ad, DUMP_ALN_FIELDS, ned_off)
+    m, k = rows.shape[0], max(1, khits)
+    out = {"read_index": reads.astype(np.float64)}
+    out.update({f: hdr[f].astype(np.float64) for f in DUMP_READ_FIELDS})
+    alns = {f: np.zeros((m, k), dtype=np.float64) for f in DUMP_ALN_FIELDS}
+    edits = []
+    for i in range(m):
+        slot = int(hdr["pad2"][i] >> 16) * 8 or C.sizeof(b.Aln)
+        for j in range(min(int(hdr["nreport"][i]), k)):
+            o = hoff + j * slot
+            a = rows[i, o:o + ned_off].view(head_dt)[0]
+            for f in DUMP_ALN_FIELDS:
+                alns[f][i, j] = a[f]
+            ne = int(a["nned"])
+            e = rows[i, o + ned_off:o + ned_off + ne * ed.itemsize].view(ed)
+            edits.append(np.stack([np.full(ne, i), np.full(ne, j)] + [e[f] for f in DUMP_EDIT_FIELDS], axis=1).astype(np.float64))
+    out.update({"aln_" + f: v for f, v in alns.items()})
+    ed_all = np.concatenate(edits) if edits else np.zeros((0, 2 + len(DUMP_EDIT_FIELDS)))
+    # at most DUMP_BYTES in all: the longest prefix of the sample that fits
+    per_read = 8 * (1 + len(DUMP_READ_FIELDS) + k * len(DUMP_ALN_FIELDS)) + 8 * ed_all.shape[1] * np.bincount(ed_all[:, 0].astype(np.int64), minlength=m)
+    keep = int(np.searchsorted(np.cumsum(per_read), DUMP_BYTES, side="right"))
+    out = {f: v[:keep] for f, v in out.items()}
+    ed_all = ed_all[ed_all[:, 0] < keep]
+    for c, f in enumerate(("read", "slot") + DUMP_EDIT_FIELDS):
+        out["edit_" + f] = np.ascontiguousarray(ed_all[:, c])
+    os.makedirs(d, exist_ok=True)
+    for f, v in out.items():
+        np.save(os.path.join(d, f + ".npy"), v)
+    return len(out), sum(v.nbytes for v in out.values()), keep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1032,6 +1108,8 @@ def main():
     ap.add_argument("--index-base", default=None, help="an existing bowtie2 index (<base>.1.bt2[l] ...): used as it is; the sequence reads are sampled from is recovered from its .3/.4 files")
     ap.add_argument("--check-determinism", action="store_true", help="diagnostic: align the resident batch twice more after the timed region and compare the result records byte for byte (config.determinism)")
     ap.add_argument("--reads-fastq", default=None, help="reads of one length from this FASTQ file (names, qualities and all) instead of the generator")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the result records of the last timed step (rank 0's batch; a fixed, "
+                    "seeded sample of its reads, at most 64 MB) as float64 DIR/<name>.npy, for comparing two builds output for output (dump_outputs)")
     args = ap.parse_args()
     if args.paired:
         args.config = "pe-sens"
@@ -1246,6 +1324,12 @@ def main():
                         kern_times.append(ctx.align_timing(on_current_stream=True))
                     issued[k] = 0
     dt = sorted(rep_dts)[len(rep_dts) // 2]
+    if args.dump_outputs and rank == 0:
+        # the records of the last timed step, before anything else is issued: the sampled rows only leave the device
+        dump_reads = dump_sample(n)
+        dump_rows = last["res"].view(n, last["stride"])[torch.from_numpy(dump_reads).to(dev)].cpu().numpy()
+        nf, nb, nr = dump_outputs(args.dump_outputs, dump_rows, dump_reads, P.khits)
+        log("[bench] --dump-outputs: %d arrays, %.1f MB, result records of %d of the %d reads of the last timed step -> %s" % (nf, nb / 1e6, nr, n, args.dump_outputs))
     batch_ms = sum(a.elapsed_time(bb) for a, bb in stage_events) / len(stage_events)
     kavg = {k: sum(t[k] for t in kern_times) / len(kern_times) for k in kern_times[0]}
     cnt = ctx.counters()

@@ -111,3 +111,58 @@ def test_host_threads_per_rank():
     assert "LOCAL_WORLD_SIZE" in src and 'usable_cores() // max(1, local_world)' in src
     for lw in (1, 2, 8, 64):
         assert max(1, cores // lw) * min(lw, cores) <= max(cores, lw)       # N ranks never ask for more threads than the node has cores (beyond one each)
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def test_dump_outputs(tmp_path):
+    """--dump-outputs DIR: after the timed steps rank 0 writes the decoded records of its last timed step as float64 DIR/<name>.npy (here the stand-in's records)."""
+    import numpy as np
+    out = tmp_path / "dump"
+    d, err, cache = run_dry(tmp_path, 2, ["--dump-outputs", str(out)])
+    assert d["steps"] == 3 and "--dump-outputs: 37 arrays" in err
+    arrs = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert len(arrs) == 37 and all(a.dtype == np.float64 for a in arrs.values())
+    assert arrs["read_index"].tolist() == list(range(3000)) and arrs["aligned"].tolist() == [1.0] * 3000      # rank 0's batch, whole: it is below the sample size
+    assert arrs["aln_refoff"].shape == (3000, 1) and arrs["edit_pos"].shape == (0,)
+    shutil.rmtree(cache, ignore_errors=True)
+
+
+def test_dump_outputs_decodes_records(tmp_path):
+    """dump_outputs on hand-made records: header fields, alignment slots up to nreport (including a record whose slots have the long-read class's
+    size), the edits of each slot, and the 64 MB cap (the longest prefix of the sample that fits); the sample of a large batch is fixed."""
+    import ctypes as C
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bowtie2_amd as b
+    bench = _bench_module()
+    assert (bench.dump_sample(10 ** 6) == bench.dump_sample(10 ** 6)).all() and len(bench.dump_sample(10 ** 6)) == bench.DUMP_READS
+    khits, hoff, ned_off = 3, C.sizeof(b.ReadResult) - C.sizeof(b.Aln), b.Aln.ned.offset
+    long_slot = (C.sizeof(b.Aln) + (640 - b.MAX_EDITS) * C.sizeof(b.Edit) + 7) & ~7
+    rows = np.zeros((5, hoff + khits * long_slot), np.uint8)
+    for i in range(5):
+        r = b.ReadResult.from_buffer(rows[i])
+        slot = long_slot if i == 4 else C.sizeof(b.Aln)
+        r.aligned, r.best, r.nreport, r.pad2 = 1, -10 - i, min(i, khits), (slot // 8) << 16 | 7
+        for j in range(r.nreport):
+            a = b.Aln.from_buffer(rows[i], hoff + j * slot)
+            a.refoff, a.refid, a.score, a.nned, a.fw = 3_000_000_000 + 100 * i + j, j, -i, j + 1, 1
+            for e in range(j + 1):
+                ed = b.Edit.from_buffer(rows[i], hoff + j * slot + ned_off + e * C.sizeof(b.Edit))
+                ed.pos, ed.chr, ed.qchr, ed.type = 10 * i + e, ord("A"), ord("C"), 3
+    nf, nb, kept = bench.dump_outputs(str(tmp_path / "d"), rows, np.arange(5) * 7, khits)
+    L = lambda f: np.load(tmp_path / "d" / (f + ".npy"))
+    assert (nf, kept) == (37, 5) and L("read_index").tolist() == [0, 7, 14, 21, 28] and L("best").tolist() == [-10, -11, -12, -13, -14]
+    assert L("aln_refoff")[4].tolist() == [3_000_000_400, 3_000_000_401, 3_000_000_402] and L("aln_refoff")[1].tolist() == [3_000_000_100, 0, 0]
+    assert L("aln_nned").tolist() == [[0, 0, 0], [1, 0, 0], [1, 2, 0], [1, 2, 3], [1, 2, 3]]
+    ed = np.stack([L("edit_" + f) for f in ("read", "slot", "pos", "chr", "qchr", "type")], axis=1)
+    assert len(ed) == 1 + 3 + 6 + 6 and ed[-1].tolist() == [4, 2, 42, 65, 67, 3]
+    bench.DUMP_BYTES = 700
+    nf, nb, kept = bench.dump_outputs(str(tmp_path / "c"), rows, np.arange(5), khits)
+    assert kept == 1 and nb <= 700

@@ -13,7 +13,7 @@ from bt2test import have_ref, ref_bin, build_hostsim
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "bowtie2_amd", "bin")
 GOLD = os.path.join(ROOT, "tests", "golden")
-WRAPPER = "/root/reference/bowtie2"
+WRAPPER = ref_bin("bowtie2")      # the reference's wrapper, installed into oracle/_ref by oracle/Makefile
 
 
 def need_bin():
